@@ -8,14 +8,18 @@ add_points_batch/add_points_in_hierarchy for every batch) from the resident
 input to finished cell images in HBM (grid winners, overflow lists, headers'
 values, metadata values).  File writing is not part of a step.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run (--gpus 1 --steps K --warmup W)
+sets up, warms up, times the K steps and prints the line; --dump-outputs DIR
+also writes the cloud of the last timed step (dump_outputs).  Extra objects:
   roofline     — dominant kernel (dense slab kernel, k_slab): algorithmic
                  bytes (32 B per arrival it processes) / its
-                 summed HIP-event duration on the engine stream;
-  cpu_baseline — the C oracle (sequential restatement, 1 thread, in memory =
-                 SURVEY §8d mode (B)) on a bounded sample of the same workload
-                 at its density (config 4: the points of one level-1 cell;
-                 --cpu-full: every level-0 part of the whole run, summed).
+                 summed HIP-event duration on the engine stream, taken from
+                 the timed steps themselves;
+  cpu_baseline — with --full only: the C oracle (sequential restatement, 1
+                 thread, in memory = SURVEY §8d mode (B)) on a bounded sample
+                 of the same workload at its density (config 4: the points of
+                 one level-1 cell; --cpu-full: every level-0 part of the whole
+                 run, summed), and speedup_vs_cpu; --cpu-mode-a beside it.
 """
 import argparse
 import json
@@ -54,7 +58,18 @@ def parse():
     ap.add_argument("--merge-prior", type=int, default=0,
                     help="config 5: merge --points new points (seed --seed) into a cloud built from this many "
                          "config-4 points (seed 4); 0 = fresh build")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else this bench measures: the CPU baselines "
+                         "(cpu_baseline from --cpu-sample / --cpu-full, --cpu-mode-a) and the speed-ups against "
+                         "them; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step built (dump_outputs) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.cpu_full or args.cpu_mode_a) and not args.full:
+        ap.error("--cpu-full and --cpu-mode-a are measured with --full")
+    return args
 
 
 def host_cpu():
@@ -316,6 +331,99 @@ def record(args, n_gpus, ms, st_levels, st_cells, st_slabs, arrivals, k, dense_m
     }
 
 
+DUMP_SAMPLE_BYTES = 40 << 20   # aimed size of the two point samples together (the files stay under 64 MB)
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def _sample_mask(pts, rate):
+    """Which points of a POINT_DTYPE array belong to the sample: a hash of the
+    coordinates' bits falls on a multiple of `rate`.  It depends on the point
+    alone, not on where the build stored it."""
+    import numpy as np
+    if rate <= 1:
+        return np.ones(len(pts), dtype=bool)
+    w = pts.view(np.uint32).reshape(-1, 4)
+    h = w[:, 0] * np.uint32(0x9E3779B1)
+    h ^= w[:, 1] * np.uint32(0x85EBCA77)
+    h ^= w[:, 2] * np.uint32(0xC2B2AE3D)
+    h ^= h >> np.uint32(15)
+    h *= np.uint32(0x2C1B3C6D)
+    h ^= h >> np.uint32(12)
+    return h % np.uint32(rate) == 0
+
+
+def _rows(pts, cell):
+    """POINT_DTYPE records as float32 rows (cell row, x, y, z, r, g, b, a)."""
+    import numpy as np
+    out = np.empty((len(pts), 8), dtype=np.float32)
+    out[:, 0] = cell
+    out[:, 1], out[:, 2], out[:, 3] = pts["x"], pts["y"], pts["z"]
+    out[:, 4:] = pts["rgba"]
+    return out
+
+
+def dump_outputs(conv, st, out_dir):
+    """--dump-outputs: the cloud the last timed build left in the converter, as a
+    caller receives it from pcc_visit_cells, in four float arrays:
+
+      stats.npy   (14,) f64  number_of_points, hierarchies, levels, cells, slabs, arrivals, grid_points,
+                             kept_points, bbox_min[3], bbox_max[3]
+      cells.npy   (C, 51) f64, EVERY cell, ordered by (hierarchy, x, y, z): those 4, total_number_of_points,
+                             number_of_points, number_of_overflow_points, size, sub_cell_size, pos[3],
+                             entries, 8 x (child x, y, z, count; -1 past `entries`), then the sums of x, y, z
+                             over all its grid points and over all its overflow points (f64 sums of the f32
+                             values: they cover the points outside the samples)
+      grid.npy    (G, 8) f32  sample of the grid points: row of cells.npy, x, y, z, r, g, b, a; a cell's
+                             rows sorted by the points' bits (the grid's order is unspecified, pcconv.h)
+      overflow.npy (K, 8) f32 sample of the overflow lists, same columns, in stored order (entry after
+                             entry, each list as stored: cell.rs:108-153 keeps arrival order)
+
+    The samples are the points whose coordinate hash falls on a multiple of a
+    rate fixed by the cloud's size (all points when they fit), so two builds of
+    the same input yield the same rows."""
+    import numpy as np
+    import pcconv
+    total = int(st["grid_points"]) + int(st["kept_points"])
+    rate = max(1, -(-total * 32 // DUMP_SAMPLE_BYTES))
+    heads, grids, overs = [], [], []
+
+    def visit(ptr):
+        v = pcconv.CellView.from_address(ptr)
+        row = [v.hierarchy, v.x, v.y, v.z, v.total_number_of_points, v.number_of_points,
+               v.number_of_overflow_points, v.size, v.sub_cell_size, *v.pos, v.entries]
+        g = v.grid_points()
+        lists = v.overflow()
+        for e in range(8):
+            row += [*lists[e][0], 0 if lists[e][1] is None else len(lists[e][1])] if e < len(lists) else [-1] * 4
+        kept = [l for _, l in lists if l is not None]
+        o = np.concatenate(kept) if kept else np.empty(0, dtype=pcconv.POINT_DTYPE)
+        row += [float(p[a].sum(dtype=np.float64)) for p in (g, o) for a in "xyz"]
+        heads.append(row)
+        g = g[_sample_mask(g, rate)]
+        w = g.view(np.uint32).reshape(-1, 4)
+        grids.append(g[np.lexsort((w[:, 3], w[:, 2], w[:, 1], w[:, 0]))])
+        overs.append(o[_sample_mask(o, rate)])
+        return 0
+
+    conv.visit_cells(visit)
+    cells = np.asarray(heads, dtype=np.float64).reshape(-1, 51)
+    order = np.lexsort((cells[:, 3], cells[:, 2], cells[:, 1], cells[:, 0]))
+    arrays = {
+        "stats": np.asarray([st[k] for k in ("number_of_points", "hierarchies", "levels", "cells", "slabs", "arrivals",
+                                             "grid_points", "kept_points")] + st["bbox_min"] + st["bbox_max"],
+                            dtype=np.float64),
+        "cells": cells[order],
+        "grid": np.concatenate([_rows(grids[k], i) for i, k in enumerate(order)] or [np.empty((0, 8), np.float32)]),
+        "overflow": np.concatenate([_rows(overs[k], i) for i, k in enumerate(order)] or [np.empty((0, 8), np.float32)]),
+    }
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {size} bytes, over the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main_sharded(args, rank, world):
     """N > 1: one rank per GPU (torchrun), level-0 cells sharded, RCCL exchange."""
     import torch
@@ -478,6 +586,9 @@ def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if args.dump_outputs and (world > 1 or os.environ.get("PCC_BENCH_OWNER") == "1"
+                              or os.environ.get("PCC_BENCH_SHARDED") == "1"):
+        sys.exit("bench.py: --dump-outputs writes the single-GPU build's cloud; the N > 1 paths keep theirs per rank")
     # (PCC_BENCH_OWNER=1: the owner path at N = 1 too, its RCCL calls on one rank -- a check)
     if (world > 1 or os.environ.get("PCC_BENCH_OWNER") == "1") and not args.exchange and not args.merge_prior:
         args.gpus = world
@@ -510,15 +621,17 @@ def main():
         st = conv.build()
         prof.append(conv.kernel_times())
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(conv, st, args.dump_outputs)
     conv.close()
     ms = 1000.0 * el / args.steps
     dense_ms = sum(p["dense_ms"] for p in prof) / len(prof)
     res = record(args, 1, ms, st["levels"], st["cells"], st["slabs"], st["arrivals"], prof[-1], dense_ms,
                  "single GPU")
-    if args.cpu_full:
+    if args.full and args.cpu_full:
         res["cpu_baseline"] = cpu_full_mode_b(args)
         res["speedup_vs_cpu"] = res["value"] / res["cpu_baseline"]["value"]
-    elif args.cpu_sample > 0:
+    elif args.full and args.cpu_sample > 0:
         res["cpu_baseline"] = cpu_baseline(args)
         res["speedup_vs_cpu"] = res["value"] / res["cpu_baseline"]["value"]
     if args.cpu_mode_a:

@@ -3,7 +3,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R && mkdir -p gpurun_out/mode_a
-B="python3 -u bench.py --steps 3 --warmup 1 --cpu-sample 0 --cpu-mode-a"
+B="python3 -u bench.py --steps 3 --warmup 1 --full --cpu-sample 0 --cpu-mode-a"
 timeout -k 10 200 $B --points 100000 --seed 1 > gpurun_out/mode_a/c1.json 2> gpurun_out/mode_a/c1.err || exit 1
 echo c1
 timeout -k 10 300 $B --points 10000000 --seed 2 > gpurun_out/mode_a/c2.json 2> gpurun_out/mode_a/c2.err || exit 2
