@@ -454,6 +454,50 @@ int pcc_write_metadata(pcc_converter* c);
 /* Drop all added input (and build results) but keep device allocations. */
 int pcc_clear_input(pcc_converter* c);
 
+/* ---- Multi-pass conversion: clouds larger than device memory on one GPU ------
+ * The reference converts any size through its cell cache (converter.rs:92,
+ * 160-178).  Here the level-0 subtrees, which are independent
+ * (converter.rs:32-47,114-139), are built a few at a time: every pass holds the
+ * points of some level-0 cells, at most max_resident_points of them, and
+ * builds and writes those cells' subtrees with the global batch structure. */
+
+/* Packs the level-0 cells of a grid (cell_points[dense cell id], the ids of
+ * pcc_shard_histogram) into passes of at most max_points each, first-fit
+ * decreasing (host only, no device): heaviest first, ties by cell id, each into
+ * the lowest-numbered pass that still has room.  pass_of_cell[cell] (empty
+ * cells: 0) and *npasses (>= 1).  -E2BIG: one cell alone exceeds max_points. */
+int pcc_pass_plan(const uint64_t* cell_points, uint64_t ncells, uint64_t max_points, uint32_t* pass_of_cell,
+                  uint32_t* npasses);
+
+/* One piece (n < 2^32 device points) of a pass's input: dev_out[0 .. *kept)
+ * receives, in input order, the points whose level-0 cell c (the cell id of
+ * pcc_shard_histogram over g) has dev_pass_of_cell[c] == pass.  rel[j] (host,
+ * ascending, in [0, n]) are piece-relative indices and below[j] (host) the
+ * number of selected points with index < rel[j].  -ENOSPC: more than `room`
+ * points are selected (*kept tells how many; nothing is written past room).
+ * -ERANGE: a point outside the grid or with a NaN / infinite coordinate. */
+int pcc_pass_select(const pcc_point* dev_pts, uint64_t n, const pcc_shard_grid* g, const uint32_t* dev_pass_of_cell,
+                    uint32_t pass, pcc_point* dev_out, uint64_t room, uint64_t* kept, const uint64_t* rel,
+                    uint64_t nrel, uint64_t* below, int device);
+
+typedef struct pcc_pass_report {
+    uint64_t number_of_points, cells, max_pass_points;
+    uint32_t passes, hierarchies;
+    double scan_ms, select_ms, build_ms, write_ms;
+} pcc_pass_report;
+
+/* pcc_convert_files against a cap on the points resident in device memory: a
+ * scan of the files (box, points per level-0 cell, every file's point count by
+ * the rules of lib.rs:31-52), pcc_pass_plan, then per pass a re-read of the
+ * files through pcc_pass_select, one build and pcc_write_cells; metadata.json
+ * is written last, on success only.  The output equals pcc_convert_files'.
+ * Refused: a merge into a non-empty out_dir (-ENOTSUP), NaN or infinite
+ * coordinates (-EDOM), more than 2^22 level-0 cells (-EOVERFLOW),
+ * sub_grid_dimension > 97 (-ENOTSUP), max_resident_points == 0 (-EINVAL), one
+ * level-0 cell heavier than the cap (-E2BIG). */
+int pcc_convert_files_passes(const char* out_dir, const char* const* paths, size_t npaths, const pcc_options* opt,
+                             uint64_t max_resident_points, pcc_pass_report* report /* may be NULL */);
+
 /* Thread-local message of the last failing call ("" if none). */
 const char* pcc_last_error(void);
 

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <ctime>
 #include <fstream>
+#include <functional>
 #include <memory>
 #include <sstream>
 #include <thread>
@@ -1080,6 +1081,125 @@ const pcc_point* pcc_device_input(const pcc_converter* c) {
     return c ? reinterpret_cast<const pcc_point*>(c->eng->device_input()) : nullptr;
 }
 
+// The input of a conversion as the readers deliver it (lib.rs:11-84): for each
+// file in CLI order, for each piece in file order.  A file with points is
+// begin(header count), piece()..., then end(keep) -- the file is the first
+// `keep` points delivered -- or cancel() -- it contributes nothing, not even a
+// batch; a file without points is empty_batches(k) (ASCII PLY, ply.rs:43-51) or
+// empty_file() (one empty batch).  A nonzero return from the sink stops the
+// enumeration and is returned.  log: the reference CLI's lines.
+struct FileSink {
+    std::function<int(uint64_t)> begin;
+    std::function<int(const Point*, uint64_t)> piece;
+    std::function<int(uint64_t)> end;
+    std::function<int()> cancel;
+    std::function<int(uint64_t)> empty_batches;
+    std::function<int()> empty_file;
+};
+
+static int for_each_file_piece(const char* const* paths, size_t npaths, uint64_t batch, const FileSink& S, bool log) {
+    for (size_t i = 0; i < npaths; i++) {
+        const std::string p = paths[i];
+        if (log) log_line("INFO", "Converting file %zu/%zu, \"%s\"", i + 1, npaths, p.c_str());
+        const size_t dot = p.find_last_of('.');
+        const size_t slash = p.find_last_of('/');
+        std::string ext = (dot == std::string::npos || (slash != std::string::npos && dot < slash)) ? "" : p.substr(dot + 1);
+        // lib.rs:31-52: a get_batch error is logged and ends that file; the batches
+        // read before it stay, the failing batch is lost, the next file follows.
+        // So a file whose data ends early contributes its complete batches only.
+        const uint64_t B = batch;
+        int rc = 0;
+        if (ext == "ply") {
+            PlyResult r;
+            std::string err;
+            bool open = false, logged = false;
+            uint64_t pushed = 0;
+            int src = 0;
+            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
+                if (!logged) { if (log) log_line("INFO", "Converting %llu points", (unsigned long long)r.vertex_count); logged = true; }
+                if (!open) { if ((src = S.begin(r.vertex_count))) return false; open = true; }
+                if ((src = S.piece(pts, m))) return false;
+                pushed += m;
+                return true;
+            };
+            const bool ok = read_ply(p, r, err, sink);
+            if (!ok || src) {
+                if (open) S.cancel();
+                return src ? src : set_err(-EIO, err);   // the reference unwraps header parsing (ply.rs:20-24)
+            }
+            if (!logged && log) log_line("INFO", "Converting %llu points", (unsigned long long)r.vertex_count);
+            if (r.ascii) {
+                const uint64_t nb = r.data_error.empty() ? std::max<uint64_t>(1, (r.vertex_count + B - 1) / B)
+                                                         : r.ascii_lines / B;
+                if (nb) rc = S.empty_batches(nb);
+            } else {
+                // lib.rs:31-52: a truncated file keeps its complete batches; none at all: no batch
+                const uint64_t keep = r.data_error.empty() ? pushed : (pushed / B) * B;
+                if (open) rc = (r.data_error.empty() || keep) ? S.end(keep) : S.cancel();
+                else if (r.data_error.empty()) rc = S.empty_file();   // an empty file: one empty batch
+            }
+            if (rc) return rc;
+            if (!r.data_error.empty() && log) log_line("ERROR", "%s", r.data_error.c_str());
+        } else if (ext == "las" || ext == "laz") {   // converter/las.rs:14-46, streamed like PLY
+            LasResult r;
+            std::string err;
+            bool open = false, logged = false;
+            uint64_t pushed = 0;
+            int src = 0;
+            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
+                if (!logged) { if (log) log_line("INFO", "Converting %llu points", (unsigned long long)r.count); logged = true; }
+                if (!open) { if ((src = S.begin(r.count))) return false; open = true; }
+                if ((src = S.piece(pts, m))) return false;
+                pushed += m;
+                return true;
+            };
+            const bool ok = read_las(p, r, err, sink);
+            if (!ok || src) {
+                if (open) S.cancel();
+                return src ? src : set_err(-EIO, err);   // the reference unwraps Reader::from_path (las.rs:16)
+            }
+            if (!r.laz_error.empty()) {
+                if (log) log_line("ERROR", "%s", r.laz_error.c_str());
+                continue;
+            }
+            if (!logged && log) log_line("INFO", "Converting %llu points", (unsigned long long)r.count);
+            const uint64_t keep = r.data_error.empty() ? pushed : (pushed / B) * B;
+            if (open) rc = (r.data_error.empty() || keep) ? S.end(keep) : S.cancel();
+            else if (r.data_error.empty()) rc = S.empty_file();   // no points: one empty batch
+            if (rc) return rc;
+            if (!r.data_error.empty() && log) log_line("ERROR", "%s", r.data_error.c_str());
+        } else if (ext == "json") {   // converter/own.rs: another converted cloud as input, streamed
+            uint64_t total = 0, pushed = 0;
+            std::string err;
+            bool open = false, logged = false;
+            int src = 0;
+            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
+                if (!logged) { if (log) log_line("INFO", "Converting %llu points", (unsigned long long)total); logged = true; }
+                if (!open) { if ((src = S.begin(total))) return false; open = true; }
+                if ((src = S.piece(pts, m))) return false;
+                pushed += m;
+                return true;
+            };
+            const int r = read_cloud_points(p, total, sink, err);
+            if (src) {   // the sink refused a piece
+                if (open) S.cancel();
+                return src;
+            }
+            if (r) {   // lib.rs:75-77 unwraps; reported instead, the file contributes nothing
+                if (open) S.cancel();
+                if (log) log_line("ERROR", "%s", err.c_str());
+                continue;
+            }
+            if (!logged && log) log_line("INFO", "Converting %llu points", (unsigned long long)total);
+            rc = open ? S.end(pushed) : S.empty_file();   // an empty cloud: one empty batch
+            if (rc) return rc;
+        } else {
+            if (log) log_line("WARN", "Unsupported file format '%s'", ext.c_str());   // lib.rs:78-81
+        }
+    }
+    return 0;
+}
+
 // lib.rs:11-60 convert_from_paths
 int pcc_convert_files(const char* out_dir, const char* const* paths, size_t npaths, const pcc_options* opt) {
     pcc_converter* c = nullptr;
@@ -1116,114 +1236,476 @@ int pcc_convert_files(const char* out_dir, const char* const* paths, size_t npat
         }
         if (total && total < (1ull << 31)) (void)pcc_reserve(c, total);
     }
-    for (size_t i = 0; i < npaths; i++) {
-        const std::string p = paths[i];
-        log_line("INFO", "Converting file %zu/%zu, \"%s\"", i + 1, npaths, p.c_str());
-        const size_t dot = p.find_last_of('.');
-        const size_t slash = p.find_last_of('/');
-        std::string ext = (dot == std::string::npos || (slash != std::string::npos && dot < slash)) ? "" : p.substr(dot + 1);
-        // lib.rs:31-52: a get_batch error is logged and ends that file; the batches
-        // read before it stay, the failing batch is lost, the next file follows.
-        // So a file whose data ends early contributes its complete batches only.
-        const uint64_t B = c->opt.batch_size;
-        if (ext == "ply") {
-            // streamed: the reader's pieces go through the pinned ring to the
-            // device while the next piece is read (HIP-stream upload scheduler)
-            PlyResult r;
-            std::string err;
-            bool open = false, logged = false;
-            uint64_t pushed = 0;
-            int src = 0;
-            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
-                if (!logged) { log_line("INFO", "Converting %llu points", (unsigned long long)r.vertex_count); logged = true; }
-                if (!open) { if ((src = pcc_begin_file(c, r.vertex_count))) return false; open = true; }
-                if ((src = pcc_append_points(c, reinterpret_cast<const pcc_point*>(pts), m))) return false;
-                pushed += m;
-                return true;
-            };
-            const bool ok = read_ply(p, r, err, sink);
-            if (!ok || src) {
-                if (open) pcc_cancel_file(c);
-                pcc_close(c);
-                return src ? src : set_err(-EIO, err);   // the reference unwraps header parsing (ply.rs:20-24)
-            }
-            if (!logged) log_line("INFO", "Converting %llu points", (unsigned long long)r.vertex_count);
-            if (r.ascii) {
-                const uint64_t nb = r.data_error.empty() ? std::max<uint64_t>(1, (r.vertex_count + B - 1) / B)
-                                                         : r.ascii_lines / B;
-                if (nb) rc = pcc_add_empty_batches(c, (uint32_t)nb);
-            } else {
-                // lib.rs:31-52: a truncated file keeps its complete batches; none at all: no batch
-                const uint64_t keep = r.data_error.empty() ? pushed : (pushed / B) * B;
-                if (open) rc = (r.data_error.empty() || keep) ? pcc_end_file(c, keep) : pcc_cancel_file(c);
-                else if (r.data_error.empty()) rc = pcc_add_points(c, nullptr, 0);   // an empty file: one empty batch
-            }
-            if (rc) { pcc_close(c); return rc; }
-            if (!r.data_error.empty()) log_line("ERROR", "%s", r.data_error.c_str());
-        } else if (ext == "las" || ext == "laz") {   // converter/las.rs:14-46, streamed like PLY
-            LasResult r;
-            std::string err;
-            bool open = false, logged = false;
-            uint64_t pushed = 0;
-            int src = 0;
-            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
-                if (!logged) { log_line("INFO", "Converting %llu points", (unsigned long long)r.count); logged = true; }
-                if (!open) { if ((src = pcc_begin_file(c, r.count))) return false; open = true; }
-                if ((src = pcc_append_points(c, reinterpret_cast<const pcc_point*>(pts), m))) return false;
-                pushed += m;
-                return true;
-            };
-            const bool ok = read_las(p, r, err, sink);
-            if (!ok || src) {
-                if (open) pcc_cancel_file(c);
-                pcc_close(c);
-                return src ? src : set_err(-EIO, err);   // the reference unwraps Reader::from_path (las.rs:16)
-            }
-            if (!r.laz_error.empty()) {
-                log_line("ERROR", "%s", r.laz_error.c_str());
-                continue;
-            }
-            if (!logged) log_line("INFO", "Converting %llu points", (unsigned long long)r.count);
-            const uint64_t keep = r.data_error.empty() ? pushed : (pushed / B) * B;
-            if (open) rc = (r.data_error.empty() || keep) ? pcc_end_file(c, keep) : pcc_cancel_file(c);
-            else if (r.data_error.empty()) rc = pcc_add_points(c, nullptr, 0);   // no points: one empty batch
-            if (rc) { pcc_close(c); return rc; }
-            if (!r.data_error.empty()) log_line("ERROR", "%s", r.data_error.c_str());
-        } else if (ext == "json") {   // converter/own.rs: another converted cloud as input, streamed
-            uint64_t total = 0, pushed = 0;
-            std::string err;
-            bool open = false, logged = false;
-            int src = 0;
-            const PointSink sink = [&](const Point* pts, uint64_t m) -> bool {
-                if (!logged) { log_line("INFO", "Converting %llu points", (unsigned long long)total); logged = true; }
-                if (!open) { if ((src = pcc_begin_file(c, total))) return false; open = true; }
-                if ((src = pcc_append_points(c, reinterpret_cast<const pcc_point*>(pts), m))) return false;
-                pushed += m;
-                return true;
-            };
-            const int r = read_cloud_points(p, total, sink, err);
-            if (src) {   // the converter refused a piece
-                if (open) pcc_cancel_file(c);
-                pcc_close(c);
-                return src;
-            }
-            if (r) {   // lib.rs:75-77 unwraps; reported instead, the file contributes nothing
-                if (open) pcc_cancel_file(c);
-                log_line("ERROR", "%s", err.c_str());
-                continue;
-            }
-            if (!logged) log_line("INFO", "Converting %llu points", (unsigned long long)total);
-            rc = open ? pcc_end_file(c, pushed) : pcc_add_points(c, nullptr, 0);   // an empty cloud: one empty batch
-            if (rc) { pcc_close(c); return rc; }
-        } else {
-            log_line("WARN", "Unsupported file format '%s'", ext.c_str());   // lib.rs:78-81
-        }
-    }
+    // streamed: the readers' pieces go through the pinned ring to the device
+    // while the next piece is read (HIP-stream upload scheduler)
+    FileSink S;
+    S.begin = [&](uint64_t expected) { return pcc_begin_file(c, expected); };
+    S.piece = [&](const Point* pts, uint64_t m) { return pcc_append_points(c, reinterpret_cast<const pcc_point*>(pts), m); };
+    S.end = [&](uint64_t keep) { return pcc_end_file(c, keep); };
+    S.cancel = [&]() { return pcc_cancel_file(c); };
+    S.empty_batches = [&](uint64_t k) { return pcc_add_empty_batches(c, (uint32_t)k); };
+    S.empty_file = [&]() { return pcc_add_points(c, nullptr, 0); };
+    rc = for_each_file_piece(paths, npaths, c->opt.batch_size, S, true);
+    if (rc) { pcc_close(c); return rc; }
     rc = pcc_build(c);
     if (rc) { pcc_close(c); return rc; }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     log_line("INFO", "Finished converting after %llu ms", (unsigned long long)ms);   // lib.rs:56-59
     return pcc_finish(c);
+}
+
+// ---- multi-pass conversion (clouds larger than device memory, one GPU) ------
+
+// First-fit decreasing over the level-0 cells' point counts.  The lowest pass
+// with room is found in a tournament tree over the passes' remaining room (a
+// pass not opened yet has all of it, and there are never more passes than
+// non-empty cells).
+int pcc_pass_plan(const uint64_t* cell_points, uint64_t ncells, uint64_t max_points, uint32_t* pass_of_cell,
+                  uint32_t* npasses) {
+    if ((ncells && (!cell_points || !pass_of_cell)) || !npasses) return set_err(-EINVAL, "null argument");
+    if (max_points == 0) return set_err(-EINVAL, "max_points must be >= 1");
+    if (ncells >= (1ull << 32)) return set_err(-EOVERFLOW, "more than 2^32-1 cells");
+    std::vector<uint64_t> order;
+    for (uint64_t i = 0; i < ncells; i++) {
+        pass_of_cell[i] = 0;
+        if (cell_points[i]) order.push_back(i);
+    }
+    *npasses = 1;
+    if (order.empty()) return 0;
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return cell_points[a] > cell_points[b]; });
+    if (cell_points[order[0]] > max_points)
+        return set_err(-E2BIG, "level-0 cell " + std::to_string(order[0]) + " alone holds " +
+                                   std::to_string(cell_points[order[0]]) + " points, more than the cap of " +
+                                   std::to_string(max_points));
+    uint64_t m = 1;
+    while (m < order.size()) m <<= 1;
+    std::vector<uint64_t> room(2 * m, max_points);   // room[m + p]: pass p; an inner node: the most room below it
+    uint32_t used = 0;
+    for (uint64_t i : order) {
+        const uint64_t w = cell_points[i];
+        uint64_t v = 1;
+        while (v < m) v = room[2 * v] >= w ? 2 * v : 2 * v + 1;   // the root always has room: an unopened pass
+        const uint32_t p = (uint32_t)(v - m);
+        pass_of_cell[i] = p;
+        used = std::max(used, p + 1);
+        room[v] -= w;
+        for (v >>= 1; v >= 1; v >>= 1) room[v] = std::max(room[2 * v], room[2 * v + 1]);
+    }
+    *npasses = used;
+    return 0;
+}
+
+int pcc_pass_select(const pcc_point* d, uint64_t n, const pcc_shard_grid* g, const uint32_t* dpass_of_cell, uint32_t pass,
+                    pcc_point* dout, uint64_t room, uint64_t* kept, const uint64_t* rel, uint64_t nrel, uint64_t* below,
+                    int device) {
+    if ((!d && n) || !g || !dpass_of_cell || !kept || ((!rel || !below) && nrel) || (!dout && room && n))
+        return set_err(-EINVAL, "null argument");
+    if (n >= (1ull << 32)) return set_err(-EOVERFLOW, "a piece holds fewer than 2^32 points");
+    GUARD_BEGIN
+    const int rc = pass_select(reinterpret_cast<const Point*>(d), n, to_grid(g), dpass_of_cell, pass,
+                               reinterpret_cast<Point*>(dout), room, kept, rel, nrel, below, device);
+    if (rc == -ENOSPC)
+        return set_err(rc, "pass select: " + std::to_string(*kept) + " points selected, room for " + std::to_string(room));
+    if (rc == -ERANGE) return set_err(rc, "pass select: point outside the grid or with a NaN / infinite coordinate");
+    return rc ? set_err(rc, "pass select: boundaries must ascend within [0, n], fewer than 2^32 of them") : 0;
+    GUARD_END
+}
+
+namespace {
+// Two pinned staging buffers and two device pieces on a copy stream: the points
+// pushed are cut into pieces of `cap`, piece k's upload runs while the caller
+// decodes piece k+1, and `consume` (synchronous device work on the landed
+// piece, with the global index of its first point) runs in key order.
+struct PieceStager {
+    uint64_t cap = 0, fill = 0, next_key = 0;
+    Point* host[2] = {nullptr, nullptr};
+    Point* dev[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t st = nullptr;
+    int cur = 0;
+    bool pending[2] = {false, false};
+    uint64_t pn[2] = {0, 0}, pkey[2] = {0, 0};
+    std::function<int(const Point*, uint64_t, uint64_t)> consume;
+
+    PieceStager(int device, uint64_t piece) : cap(piece) {
+        HIP_CHECK(hipSetDevice(device));
+        HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host[b]), cap * sizeof(Point), hipHostMallocDefault));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dev[b]), cap * sizeof(Point)));
+            HIP_CHECK(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
+        }
+    }
+    ~PieceStager() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (int b = 0; b < 2; b++) {
+            if (host[b]) (void)hipHostFree(host[b]);
+            if (dev[b]) (void)hipFree(dev[b]);
+            if (ev[b]) (void)hipEventDestroy(ev[b]);
+        }
+        if (st) (void)hipStreamDestroy(st);
+    }
+    PieceStager(const PieceStager&) = delete;
+    PieceStager& operator=(const PieceStager&) = delete;
+
+    void restart() { fill = 0; next_key = 0; cur = 0; pending[0] = pending[1] = false; }
+    int land(int b) {
+        HIP_CHECK(hipEventSynchronize(ev[b]));
+        pending[b] = false;
+        return consume(dev[b], pn[b], pkey[b]);
+    }
+    int flush() {
+        if (!fill) return 0;
+        HIP_CHECK(hipMemcpyAsync(dev[cur], host[cur], fill * sizeof(Point), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipEventRecord(ev[cur], st));
+        pending[cur] = true;
+        pn[cur] = fill;
+        pkey[cur] = next_key;
+        next_key += fill;
+        fill = 0;
+        cur ^= 1;   // the other buffers are free once their piece has been consumed
+        return pending[cur] ? land(cur) : 0;
+    }
+    int push(const Point* p, uint64_t m) {
+        while (m) {
+            const uint64_t take = std::min(m, cap - fill);
+            memcpy(host[cur] + fill, p, take * sizeof(Point));
+            fill += take; p += take; m -= take;
+            if (fill == cap) {
+                const int rc = flush();
+                if (rc) return rc;
+            }
+        }
+        return 0;
+    }
+    int drain() {
+        int rc = flush();
+        for (int b = 0; b < 2 && !rc; b++)
+            if (pending[b]) rc = land(b);
+        return rc;
+    }
+};
+
+// What one input file contributes, fixed by the scan (lib.rs:31-52).
+struct FileShare {
+    uint64_t keep = 0;      // its first `keep` points
+    uint64_t batches = 0;   // ceil(keep / batch); without points: its empty batches (0: nothing at all)
+};
+}  // namespace
+
+int pcc_convert_files_passes(const char* out_dir, const char* const* paths, size_t npaths, const pcc_options* opt,
+                             uint64_t max_resident_points, pcc_pass_report* report) {
+    if (!out_dir || (!paths && npaths)) return set_err(-EINVAL, "null argument");
+    if (report) memset(report, 0, sizeof *report);
+    if (max_resident_points == 0) return set_err(-EINVAL, "max_resident_points must be >= 1");
+    pcc_options o;
+    if (opt) o = *opt; else pcc_options_default(&o);
+    if (o.batch_size == 0) return set_err(-EINVAL, "batch_size must be >= 1");
+    {
+        std::ifstream f(std::string(out_dir) + "/metadata.json");
+        if (f) log_line("INFO", "Found an existing metadata file.");
+        else log_line("INFO", "Found no metadata file. A new one will be created.");
+    }
+    if (any_cell_file(out_dir))
+        return set_err(-ENOTSUP, "multi-pass conversion cannot merge into the existing cloud in " + std::string(out_dir));
+    pcc_converter* c = nullptr;
+    int rc = pcc_open(out_dir, &o, &c);
+    if (rc) return rc;
+    struct Close {
+        pcc_converter* c;
+        ~Close() { pcc_close(c); }
+    } closer{c};
+    if (c->merge)
+        return set_err(-ENOTSUP, "multi-pass conversion cannot merge into the existing cloud in " + std::string(out_dir));
+    if (c->meta.config.sub_grid_dimension > 97)
+        return set_err(-ENOTSUP, "multi-pass conversion: sub_grid_dimension > 97 is not supported");
+    GUARD_BEGIN
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = clk::now();
+    const uint64_t B = c->opt.batch_size;
+    const int device = c->opt.device;
+    uint64_t piece = 1ull << 22;
+    if (const char* e = getenv("PCC_TEST_PASS_PIECE")) {   // tests: small pieces cross batch and file boundaries
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v) piece = std::min<uint64_t>(v, 1ull << 28);
+    }
+    PieceStager stage(device, piece);
+
+    // ---- scan: every file's share, the box, the points per level-0 cell ----
+    std::vector<FileShare> files;
+    float bmin[3] = {INFINITY, INFINITY, INFINITY}, bmax[3] = {-INFINITY, -INFINITY, -INFINITY};
+    ShardGrid guess{};
+    bool guessed = false, guess_ok = false;
+    uint32_t* dhist = nullptr;
+    struct FreeDev {
+        uint32_t*& p;
+        ~FreeDev() { if (p) (void)hipFree(p); }
+    } free_hist{dhist};
+    std::vector<uint32_t> h32;
+    std::vector<uint64_t> hguess;
+    stage.consume = [&](const Point* d, uint64_t n, uint64_t) -> int {
+        float lo[3], hi[3];
+        int r = shard_bbox(d, n, lo, hi, device);
+        if (r) return set_err(r, "multi-pass conversion: the input has NaN or infinite coordinates");
+        for (int a = 0; a < 3; a++) { bmin[a] = std::fmin(bmin[a], lo[a]); bmax[a] = std::fmax(bmax[a], hi[a]); }
+        if (!guessed) {   // the grid of the first piece's box, one cell of margin: the true grid is rarely larger
+            guessed = true;
+            pcc_shard_grid pg;
+            if (pcc_shard_grid_from_bbox(lo, hi, c->meta.config.max_cell_size, &pg) == 0) {
+                uint64_t nc = 1;
+                for (int a = 0; a < 3; a++) nc *= (uint64_t)pg.dims[a] + 2;
+                bool fits = nc <= (1ull << 22);
+                for (int a = 0; a < 3; a++) fits = fits && pg.lo[a] > INT32_MIN && pg.dims[a] < 0xFFFFFFFEu;
+                if (fits) {
+                    for (int a = 0; a < 3; a++) { pg.lo[a] -= 1; pg.dims[a] += 2; }
+                    guess = to_grid(&pg);
+                    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dhist), nc * 4));
+                    h32.resize(nc);
+                    hguess.assign(nc, 0);
+                    guess_ok = true;
+                }
+            }
+        }
+        if (guess_ok) {
+            r = shard_histogram(d, n, guess, dhist, device);
+            if (r == -ERANGE) { guess_ok = false; return 0; }   // a point outside the guess: histogram in a second read
+            if (r) return set_err(r, "multi-pass conversion: level-0 histogram failed");
+            HIP_CHECK(hipMemcpy(h32.data(), dhist, h32.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < h32.size(); i++) hguess[i] += h32[i];
+        }
+        return 0;
+    };
+    std::vector<Point> hold;   // the open file's points not yet known to be kept (its incomplete last batch)
+    uint64_t seen = 0, released = 0;
+    FileSink S;
+    S.begin = [&](uint64_t) { hold.clear(); seen = released = 0; return 0; };
+    S.piece = [&](const Point* pts, uint64_t m) -> int {
+        // a truncated file keeps its complete batches only: release those
+        const uint64_t upto = ((seen + m) / B) * B;
+        seen += m;
+        if (upto > released) {
+            int r = hold.empty() ? 0 : stage.push(hold.data(), hold.size());
+            if (r) return r;
+            released += hold.size();
+            hold.clear();
+            const uint64_t take = upto - released;
+            if ((r = stage.push(pts, take))) return r;
+            released = upto;
+            pts += take;
+            m -= take;
+        }
+        hold.insert(hold.end(), pts, pts + m);
+        return 0;
+    };
+    S.end = [&](uint64_t keep) -> int {
+        if (keep < released || keep > seen) return set_err(-EIO, "multi-pass conversion: reader kept an unexpected count");
+        const int r = stage.push(hold.data(), keep - released);
+        hold.clear();
+        files.push_back({keep, (keep + B - 1) / B});
+        return r;
+    };
+    S.cancel = [&]() { hold.clear(); files.push_back({0, 0}); return 0; };
+    S.empty_batches = [&](uint64_t k) { files.push_back({0, k}); return 0; };
+    S.empty_file = [&]() { files.push_back({0, 1}); return 0; };
+    rc = for_each_file_piece(paths, npaths, B, S, true);
+    if (!rc) rc = stage.drain();
+    if (rc) return rc;
+    uint64_t n_total = 0, total_batches = 0;
+    for (const FileShare& f : files) { n_total += f.keep; total_batches += f.batches; }
+    if (n_total != stage.next_key) return set_err(-EIO, "multi-pass conversion: scan lost count of the input");
+    if (total_batches > 0xFFFFFFFFull) return set_err(-EOVERFLOW, "more than 2^32-1 batches");
+
+    // later reads deliver exactly the scan's shares, in global key order
+    size_t fidx = 0;
+    uint64_t fseen = 0;
+    bool changed = false;
+    FileSink R;
+    R.begin = [&](uint64_t) { fseen = 0; return 0; };
+    R.piece = [&](const Point* pts, uint64_t m) -> int {
+        if (fidx >= files.size()) { changed = true; return 0; }
+        const uint64_t keep = files[fidx].keep;
+        const uint64_t take = fseen < keep ? std::min(m, keep - fseen) : 0;
+        fseen += m;
+        return take ? stage.push(pts, take) : 0;
+    };
+    auto next_file = [&]() {
+        if (fidx >= files.size() || fseen < files[fidx].keep) changed = true;
+        fidx++;
+        fseen = 0;
+        return 0;
+    };
+    R.end = [&](uint64_t) { return next_file(); };
+    R.cancel = [&]() { return next_file(); };
+    R.empty_batches = [&](uint64_t) { return next_file(); };
+    R.empty_file = [&]() { return next_file(); };
+    auto reread = [&]() -> int {
+        fidx = 0;
+        fseen = 0;
+        changed = false;
+        stage.restart();
+        int r = for_each_file_piece(paths, npaths, B, R, false);
+        if (!r) r = stage.drain();
+        if (r) return r;
+        if (changed || fidx != files.size() || stage.next_key != n_total)
+            return set_err(-EIO, "multi-pass conversion: the input files changed between two reads");
+        return 0;
+    };
+
+    // ---- the level-0 grid of the global box and its cells' point counts ----
+    pcc_shard_grid pg{};
+    std::vector<uint64_t> hist;
+    if (n_total) {
+        rc = pcc_shard_grid_from_bbox(bmin, bmax, c->meta.config.max_cell_size, &pg);
+        if (rc == -EFBIG) return set_err(-EOVERFLOW, "multi-pass conversion: the level-0 grid exceeds 2^22 cells");
+        if (rc) return rc;
+    } else {
+        pg.dims[0] = pg.dims[1] = pg.dims[2] = 1;
+        pg.cell_size = cell_size(c->meta.config.max_cell_size, 0);
+    }
+    const ShardGrid grid = to_grid(&pg);
+    const uint64_t ncells = (uint64_t)pg.dims[0] * pg.dims[1] * pg.dims[2];
+    hist.assign(ncells, 0);
+    if (n_total && guess_ok) {   // every point fell inside the guess, which therefore contains the grid
+        for (uint32_t x = 0; x < pg.dims[0]; x++)
+            for (uint32_t y = 0; y < pg.dims[1]; y++)
+                for (uint32_t z = 0; z < pg.dims[2]; z++) {
+                    const uint64_t gx = (uint64_t)((int64_t)pg.lo[0] + x - guess.lo[0]);
+                    const uint64_t gy = (uint64_t)((int64_t)pg.lo[1] + y - guess.lo[1]);
+                    const uint64_t gz = (uint64_t)((int64_t)pg.lo[2] + z - guess.lo[2]);
+                    hist[((uint64_t)x * pg.dims[1] + y) * pg.dims[2] + z] =
+                        hguess[(gx * guess.dims[1] + gy) * guess.dims[2] + gz];
+                }
+    } else if (n_total) {
+        if (dhist) { (void)hipFree(dhist); dhist = nullptr; }
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dhist), ncells * 4));
+        h32.resize(ncells);
+        stage.consume = [&](const Point* d, uint64_t n, uint64_t) -> int {
+            const int r = shard_histogram(d, n, grid, dhist, device);
+            if (r) return set_err(r, "multi-pass conversion: level-0 histogram failed (input changed between reads?)");
+            HIP_CHECK(hipMemcpy(h32.data(), dhist, ncells * 4, hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < ncells; i++) hist[i] += h32[i];
+            return 0;
+        };
+        rc = reread();
+        if (rc) return rc;
+    }
+    if (dhist) { (void)hipFree(dhist); dhist = nullptr; }
+    {
+        uint64_t sum = 0;
+        for (uint64_t v : hist) sum += v;
+        if (sum != n_total) return set_err(-EIO, "multi-pass conversion: the cell counts do not add up to the input");
+    }
+    const auto t_scan = clk::now();
+
+    // ---- plan ----
+    std::vector<uint32_t> pass_of_cell(ncells, 0);
+    uint32_t npasses = 1;
+    rc = pcc_pass_plan(hist.data(), ncells, max_resident_points, pass_of_cell.data(), &npasses);
+    if (rc == -E2BIG) {
+        const uint64_t h = std::max_element(hist.begin(), hist.end()) - hist.begin();
+        const int64_t z = h % pg.dims[2], y = (h / pg.dims[2]) % pg.dims[1], x = h / ((uint64_t)pg.dims[2] * pg.dims[1]);
+        return set_err(-E2BIG, "level-0 cell (" + std::to_string(pg.lo[0] + x) + ", " + std::to_string(pg.lo[1] + y) + ", " +
+                                   std::to_string(pg.lo[2] + z) + ") alone holds " + std::to_string(hist[h]) +
+                                   " points, more than max_resident_points = " + std::to_string(max_resident_points));
+    }
+    if (rc) return rc;
+    std::vector<uint64_t> pass_points(npasses, 0);
+    for (uint64_t i = 0; i < ncells; i++) pass_points[pass_of_cell[i]] += hist[i];
+    const uint64_t max_pass = *std::max_element(pass_points.begin(), pass_points.end());
+    if (max_pass >= 0xFFFFFFFFull) return set_err(-EOVERFLOW, "a pass of 2^32-1 points or more: lower max_resident_points");
+
+    // the global batches that hold points (lib.rs:31-52): first key and event batch number
+    std::vector<uint64_t> gstart;
+    std::vector<uint32_t> gbatch;
+    {
+        uint64_t key = 0, eb = 0;
+        for (const FileShare& f : files) {
+            for (uint64_t b = 0; b * B < f.keep; b++) { gstart.push_back(key + b * B); gbatch.push_back((uint32_t)(eb + b)); }
+            key += f.keep;
+            eb += f.batches;
+        }
+    }
+
+    // ---- passes ----
+    double select_ms = 0, build_ms = 0, write_ms = 0;
+    uint64_t cells = 0;
+    uint32_t hierarchies = 0;
+    Point* dpass = nullptr;
+    uint32_t* dpoc = nullptr;
+    struct FreeAll {
+        Point*& a;
+        uint32_t*& b;
+        ~FreeAll() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); }
+    } free_pass{dpass, dpoc};
+    if (max_pass) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dpass), max_pass * sizeof(Point)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dpoc), ncells * 4));
+    HIP_CHECK(hipMemcpy(dpoc, pass_of_cell.data(), ncells * 4, hipMemcpyHostToDevice));
+    std::vector<uint64_t> lstart(gstart.size()), rel, below;
+    for (uint32_t p = 0; p < npasses; p++) {
+        const auto tp0 = clk::now();
+        uint64_t nsel = 0;
+        size_t jb = 0;
+        stage.consume = [&](const Point* d, uint64_t n, uint64_t key0) -> int {
+            // the global batches that start inside this piece
+            const size_t j0 = jb;
+            rel.clear();
+            while (jb < gstart.size() && gstart[jb] < key0 + n) rel.push_back(gstart[jb++] - key0);
+            below.assign(rel.size(), 0);
+            uint64_t kept = 0;
+            const int r = pass_select(d, n, grid, dpoc, p, dpass + nsel, pass_points[p] - nsel, &kept, rel.data(),
+                                      rel.size(), below.data(), device);
+            if (r) return set_err(r, "multi-pass conversion: selecting a pass's points failed (input changed between reads?)");
+            for (size_t j = 0; j < rel.size(); j++) lstart[j0 + j] = nsel + below[j];
+            nsel += kept;
+            return 0;
+        };
+        if (n_total) {
+            rc = reread();
+            if (rc) return rc;
+        }
+        if (nsel != pass_points[p] || jb != gstart.size())
+            return set_err(-EIO, "multi-pass conversion: the input files changed between two reads");
+        // the pass's event table: the global batches holding some of its points
+        std::vector<uint64_t> starts;
+        std::vector<uint32_t> batches;
+        for (size_t j = 0; j < gstart.size(); j++)
+            if (lstart[j] < (j + 1 < gstart.size() ? lstart[j + 1] : nsel)) { starts.push_back(lstart[j]); batches.push_back(gbatch[j]); }
+        const auto tp1 = clk::now();
+        select_ms += ms(tp0, tp1);
+        if ((rc = pcc_clear_input(c))) return rc;
+        if ((rc = pcc_set_event_table(c, starts.data(), batches.data(), starts.size(), total_batches))) return rc;
+        if ((rc = pcc_set_keyed_points_device(c, reinterpret_cast<const pcc_point*>(dpass), nullptr, nsel))) return rc;
+        if ((rc = pcc_build(c))) return rc;
+        pcc_stats st;
+        pcc_get_stats(c, &st);
+        if (st.levels_streamed) return set_err(-EIO, "multi-pass conversion: a pass entered the streaming build");
+        hierarchies = std::max(hierarchies, c->meta.hierarchies);
+        cells += st.cells;
+        const auto tp2 = clk::now();
+        build_ms += ms(tp1, tp2);
+        if ((rc = pcc_write_cells(c))) return rc;
+        write_ms += ms(tp2, clk::now());
+        log_line("INFO", "Pass %u/%u: %llu points", p + 1, npasses, (unsigned long long)nsel);
+    }
+
+    // ---- the global metadata, on success only ----
+    if ((rc = pcc_set_summary(c, n_total, bmin, bmax, hierarchies))) return rc;
+    if ((rc = pcc_write_metadata(c))) return rc;
+    log_line("INFO", "Finished converting after %llu ms", (unsigned long long)ms(t0, clk::now()));   // lib.rs:56-59
+    if (report) {
+        report->number_of_points = n_total;
+        report->cells = cells;
+        report->max_pass_points = max_pass;
+        report->passes = npasses;
+        report->hierarchies = hierarchies;
+        report->scan_ms = ms(t0, t_scan);
+        report->select_ms = select_ms;
+        report->build_ms = build_ms;
+        report->write_ms = write_ms;
+    }
+    return 0;
+    GUARD_END
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <unistd.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <string>
@@ -79,7 +80,16 @@ int main(int argc, char** argv) {
     for (auto& f : files) p.push_back(f.c_str());
     pcc_options opt;
     pcc_options_default(&opt);
-    int rc = pcc_convert_files(out.c_str(), p.data(), p.size(), &opt);
+    // PCC_MAX_RESIDENT_POINTS (a positive integer): the cloud is converted in
+    // level-0 subtree passes of at most that many points in device memory
+    unsigned long long cap = 0;
+    if (const char* e = getenv("PCC_MAX_RESIDENT_POINTS")) {
+        char* end = nullptr;
+        cap = strtoull(e, &end, 10);
+        if (end == e || *end != '\0' || e[0] == '-') cap = 0;
+    }
+    int rc = cap ? pcc_convert_files_passes(out.c_str(), p.data(), p.size(), &opt, cap, nullptr)
+                 : pcc_convert_files(out.c_str(), p.data(), p.size(), &opt);
     if (rc) {
         fprintf(stderr, "point_converter: error %d: %s\n", rc, pcc_last_error());
         return 1;

@@ -544,6 +544,10 @@ int shard_route_hist(const Point* d, uint64_t n, const ShardGrid& g, const uint3
                      const uint32_t* dhist, Point* dsend, uint64_t* dbm, uint64_t* counts, int device, uint32_t dim);
 int shard_keys_from_bitmaps(const uint64_t* dbm, const uint64_t* nwords, const uint64_t* key0, uint32_t nsrc,
                             uint32_t* dkeys, uint64_t nkeys, int device);
+// pcc_pass_select (pcconv.h): the points of the cells with dpass_of_cell[cell] == pass, compacted in input order
+// into dout[0 .. *kept) (nothing past room), and below[j] = selected points with index < rel[j] (host arrays)
+int pass_select(const Point* d, uint64_t n, const ShardGrid& g, const uint32_t* dpass_of_cell, uint32_t pass, Point* dout,
+                uint64_t room, uint64_t* kept, const uint64_t* rel, uint64_t nrel, uint64_t* below, int device);
 // pcc_shard_resolve_buckets (pcconv.h)
 int shard_resolve_buckets(const uint64_t* seg_n, const uint32_t* seg_bucket, uint64_t nseg, uint32_t nbuckets,
                           const Point* dpts, const uint32_t* dkeys, const uint64_t* file_points, uint64_t nfiles,

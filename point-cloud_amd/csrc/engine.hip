@@ -9358,9 +9358,12 @@ struct ShardScratch {
     unsigned long long* ks = nullptr;   // its sort scratch of kept lists above kKeptMax
     uint64_t ks_cap = 0;
     uint64_t rt_cap = 0;
+    uint64_t* sel = nullptr;   // pass_select's boundaries and their answers
+    uint64_t sel_cap = 0;
     SortTemp sort;
     ~ShardScratch() {
         for (auto* b : buf) (void)hipFree(b);
+        (void)hipFree(sel);
         (void)hipFree(part); (void)hipFree(nfpart); (void)hipFree(flag); (void)hipFree(cnt); (void)hipFree(tab); (void)hipFree(rt); (void)hipFree(ks);
         (void)hipFree(sort.counts); (void)hipFree(sort.scan.bsums);
         if (st) (void)hipStreamDestroy(st);
@@ -10373,6 +10376,165 @@ int shard_route_hist(const Point* d, uint64_t n, const ShardGrid& g, const uint3
     for (uint32_t r = 0; r < nranks; r++) { counts[r] = ht[r]; sum += ht[r]; }
     if ((bad & 2u) || sum != n) return -EBADMSG;
     return bad ? -ERANGE : 0;
+}
+
+// ------------------------------------------------------------------ pass select (pcc_pass_select)
+// One destination of the route above: the points whose level-0 cell belongs to
+// `pass` (pass_of_cell[cell id of shard_unit] == pass), compacted in input
+// order.  Per 4096-point tile the selected count (k_sel_count), an exclusive
+// scan over the tiles, then every tile writes its selected points behind its
+// offset (k_sel_scatter): a tile's 16 rounds of 256 points are loaded at once,
+// the (round, wave) ballot counts are scanned in LDS, and a point's position is
+// the tile offset + that prefix + its rank in the wave's ballot.  The same
+// three terms answer "selected points with index < rel[j]" for the boundaries
+// rel[j] inside the tile, which the tile finds by a search in the sorted rel.
+// A point outside the grid or with a non-finite coordinate is never selected
+// and sets *flag.
+namespace {
+constexpr int kSelBS = 256, kSelIPT = 16, kSelTile = kSelBS * kSelIPT, kSelW = kSelBS / 64;
+
+__device__ __forceinline__ bool sel_point(const ShardGrid& g, const uint32_t* __restrict__ pass_of_cell, uint32_t pass,
+                                          const float4& v, uint32_t& bad) {
+    const ShardSlabs cells{0.0f, 0};
+    const uint32_t c = isnan(v.x) || isnan(v.y) || isnan(v.z) ? 0xFFFFFFFFu : shard_unit<false>(g, cells, v.x, v.y, v.z);
+    if (c == 0xFFFFFFFFu) { bad = 1u; return false; }
+    return pass_of_cell[c] == pass;
+}
+
+__global__ __launch_bounds__(kSelBS) void k_sel_count(const Point* __restrict__ in, uint32_t n, ShardGrid g,
+                                                      const uint32_t* __restrict__ pass_of_cell, uint32_t pass,
+                                                      uint32_t* __restrict__ counts, uint32_t* flag) {
+    __shared__ uint32_t ws[kSelW];
+    const float4* p4 = reinterpret_cast<const float4*>(in);
+    const uint64_t i0 = (uint64_t)blockIdx.x * kSelTile + threadIdx.x;
+    float4 v[kSelIPT];
+#pragma unroll
+    for (int r = 0; r < kSelIPT; r++) {
+        const uint64_t i = i0 + (uint64_t)r * kSelBS;
+        v[r] = p4[i < n ? i : n - 1];
+    }
+    uint32_t cnt = 0, bad = 0;
+#pragma unroll
+    for (int r = 0; r < kSelIPT; r++)
+        if (i0 + (uint64_t)r * kSelBS < n) cnt += sel_point(g, pass_of_cell, pass, v[r], bad) ? 1u : 0u;
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x / 64] = cnt;
+    if (bad) atomicOr(flag, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int q = 0; q < kSelW; q++) t += ws[q];
+        counts[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(kSelBS) void k_sel_scatter(const Point* __restrict__ in, uint32_t n, ShardGrid g,
+                                                        const uint32_t* __restrict__ pass_of_cell, uint32_t pass,
+                                                        const uint32_t* __restrict__ off, Point* __restrict__ out,
+                                                        uint64_t room, const unsigned long long* __restrict__ rel,
+                                                        uint32_t nrel, unsigned long long* __restrict__ below) {
+    __shared__ uint32_t wc[kSelIPT * kSelW];   // (round, wave): selected count, then its exclusive prefix in the tile
+    __shared__ unsigned long long bal[kSelIPT * kSelW];   // (round, wave): the wave's ballot of selected lanes
+    static_assert(kSelIPT * kSelW == 64, "one wave scans the (round, wave) counts");
+    const uint32_t tid = threadIdx.x, w = tid / 64, lane = tid & 63;
+    const float4* p4 = reinterpret_cast<const float4*>(in);
+    float4* o4 = reinterpret_cast<float4*>(out);
+    const uint64_t t0 = (uint64_t)blockIdx.x * kSelTile, i0 = t0 + tid;
+    float4 v[kSelIPT];
+#pragma unroll
+    for (int r = 0; r < kSelIPT; r++) {
+        const uint64_t i = i0 + (uint64_t)r * kSelBS;
+        v[r] = p4[i < n ? i : n - 1];
+    }
+    // the first boundary at or past this tile's first point (while the points load)
+    uint32_t jlo = 0;
+    for (uint32_t jhi = nrel; jlo < jhi;) {
+        const uint32_t mid = jlo + (jhi - jlo) / 2;
+        if (rel[mid] < t0) jlo = mid + 1; else jhi = mid;
+    }
+    uint32_t selbits = 0, bad = 0;
+#pragma unroll
+    for (int r = 0; r < kSelIPT; r++) {
+        const bool s = i0 + (uint64_t)r * kSelBS < n && sel_point(g, pass_of_cell, pass, v[r], bad);
+        selbits |= (s ? 1u : 0u) << r;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(s);
+        if (lane == 0) { wc[r * kSelW + w] = (uint32_t)__popcll(m); bal[r * kSelW + w] = m; }
+    }
+    __syncthreads();
+    if (tid < 64) {   // exclusive scan of the 64 counts, in (round, wave) = index order
+        const uint32_t x = wc[tid];
+        uint32_t inc = x;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(inc, d, 64);
+            if ((int)lane >= d) inc += y;
+        }
+        wc[tid] = inc - x;
+    }
+    __syncthreads();
+    const uint64_t base = off[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < kSelIPT; r++) {
+        const bool s = (selbits >> r) & 1u;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(s);
+        const uint64_t pos = base + wc[r * kSelW + w] + mask_rank(m);
+        if (s && pos < room) o4[pos] = v[r];   // past the room: -ENOSPC on the host, nothing written there
+    }
+    // the boundaries inside this tile: the selected points before index t0 + o are the
+    // tile's offset, the prefix of o's (round, wave) and the ballot's lanes below o's
+    for (uint32_t j = jlo + tid; j < nrel; j += kSelBS) {
+        const uint64_t rj = rel[j];
+        if (rj >= t0 + kSelTile) break;
+        const uint32_t o = (uint32_t)(rj - t0), q = o >> 6, l = o & 63u;
+        below[j] = base + wc[q] + (uint32_t)__popcll(bal[q] & ((1ull << l) - 1ull));
+    }
+}
+}  // namespace
+
+int pass_select(const Point* d, uint64_t n, const ShardGrid& g, const uint32_t* dpass_of_cell, uint32_t pass, Point* dout,
+                uint64_t room, uint64_t* kept, const uint64_t* rel, uint64_t nrel, uint64_t* below, int device) {
+    ShardScratch& S = shard_scratch(device);
+    if (n >= (1ull << 32) || nrel >= (1ull << 32)) return -EOVERFLOW;
+    for (uint64_t j = 0; j < nrel; j++)
+        if (rel[j] > n || (j && rel[j] < rel[j - 1])) return -EINVAL;
+    *kept = 0;
+    for (uint64_t j = 0; j < nrel; j++) below[j] = 0;
+    if (!n) return 0;
+    const uint32_t n32 = (uint32_t)n;
+    const uint32_t ntiles = (uint32_t)((n + kSelTile - 1) / kSelTile);
+    if (S.cap < (uint64_t)ntiles + 1) {
+        for (auto*& b : S.buf) { (void)hipFree(b); b = nullptr; HIP_CHECK(hipMalloc(&b, ((uint64_t)ntiles + 1) * 4)); }
+        S.cap = (uint64_t)ntiles + 1;
+    }
+    // S.sel, in 8-byte words: the total, the flag, below[nrel] (one copy back), rel[nrel]
+    if (S.sel_cap < 2 + 2 * nrel) {
+        (void)hipFree(S.sel);
+        S.sel = nullptr;
+        S.sel_cap = 0;
+        HIP_CHECK(hipMalloc(&S.sel, std::max<uint64_t>(2 + 2 * nrel, 1024) * 8));
+        S.sel_cap = std::max<uint64_t>(2 + 2 * nrel, 1024);
+    }
+    unsigned long long* dres = reinterpret_cast<unsigned long long*>(S.sel);
+    uint32_t* dtotal = reinterpret_cast<uint32_t*>(dres);
+    uint32_t* dflag = reinterpret_cast<uint32_t*>(dres + 1);
+    unsigned long long* dbelow = dres + 2;
+    unsigned long long* drel = dbelow + nrel;
+    HIP_CHECK(hipMemsetAsync(dres, 0, 16, S.st));
+    if (nrel) HIP_CHECK(hipMemcpyAsync(drel, rel, nrel * 8, hipMemcpyHostToDevice, S.st));
+    k_sel_count<<<ntiles, kSelBS, 0, S.st>>>(d, n32, g, dpass_of_cell, pass, S.buf[0], dflag);
+    scan_excl_u32(S.buf[0], S.buf[1], ntiles, dtotal, S.sort.scan, S.st);
+    k_sel_scatter<<<ntiles, kSelBS, 0, S.st>>>(d, n32, g, dpass_of_cell, pass, S.buf[1], dout, room, drel, (uint32_t)nrel,
+                                               dbelow);
+    HIP_CHECK(hipGetLastError());
+    static thread_local std::vector<unsigned long long> res;
+    res.resize(2 + nrel);
+    HIP_CHECK(hipMemcpyAsync(res.data(), dres, (2 + nrel) * 8, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
+    const uint64_t total = res[0];
+    *kept = total;
+    // a boundary at n lies in no tile when n is a multiple of the tile: everything selected is below it
+    for (uint64_t j = 0; j < nrel; j++) below[j] = rel[j] == n ? total : res[2 + j];
+    if (res[1]) return -ERANGE;
+    return total > room ? -ENOSPC : 0;
 }
 
 }  // namespace pcc

@@ -45,7 +45,7 @@ EXPORTS = ["pcc_abi_version", "pcc_last_error", "pcc_options_default", "pcc_open
            "pcc_open_subtrees", "pcc_visit_cells", "pcc_shard_route_bitmaps", "pcc_shard_route_bitmaps_hist",
            "pcc_shard_keys_from_bitmaps",
            "pcc_release_device_cache", "pcc_grid_cells", "pcc_export_grid", "pcc_shard_resolve_buckets", "pcc_shard_lpt",
-           "pcc_shard_plan_search", "pcc_reserve"]
+           "pcc_shard_plan_search", "pcc_reserve", "pcc_pass_plan", "pcc_pass_select", "pcc_convert_files_passes"]
 
 
 class Options(C.Structure):
@@ -108,6 +108,16 @@ class CellView(C.Structure):
                                                     dtype=POINT_DTYPE).copy()
             out.append((tuple(self.child[e]), lst))
         return out
+
+
+class PassReport(C.Structure):
+    """pcc_pass_report: what a multi-pass conversion did (pcc_convert_files_passes)."""
+    _fields_ = [("number_of_points", C.c_uint64), ("cells", C.c_uint64), ("max_pass_points", C.c_uint64),
+                ("passes", C.c_uint32), ("hierarchies", C.c_uint32), ("scan_ms", C.c_double),
+                ("select_ms", C.c_double), ("build_ms", C.c_double), ("write_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 CELL_VISITOR = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
@@ -203,6 +213,11 @@ def lib():
         L.pcc_adopt_prior.argtypes = [vp, vp]
         L.pcc_visit_cells.argtypes = [vp, CELL_VISITOR, vp]
         L.pcc_release_device_cache.argtypes = []
+        L.pcc_pass_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_uint32)]
+        L.pcc_pass_select.argtypes = [vp, C.c_uint64, C.POINTER(ShardGrid), vp, C.c_uint32, vp, C.c_uint64,
+                                      C.POINTER(C.c_uint64), vp, C.c_uint64, vp, C.c_int]
+        L.pcc_convert_files_passes.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(Options),
+                                               C.c_uint64, C.POINTER(PassReport)]
         L.pcc_release_device_cache.restype = C.c_uint64
         _lib = L
     return _lib
@@ -605,11 +620,44 @@ def shard_route(pts_ptr: int, n: int, key0: int, grid: ShardGrid, owner_ptr: int
     return [int(c) for c in counts]
 
 
-def convert_from_paths(paths, output: str, batch_size: int = 10_000, device: int = 0):
-    """lib.rs:11-60 convert_from_paths (PLY inputs)."""
+def pass_plan(cell_points, max_points: int):
+    """pcc_pass_plan: first-fit decreasing of the level-0 cells' point counts
+    into passes of at most max_points.  Returns (pass of each cell, passes)."""
+    w = np.ascontiguousarray(cell_points, dtype=np.uint64)
+    out = np.zeros(len(w), dtype=np.uint32)
+    npasses = C.c_uint32(0)
+    _check(lib().pcc_pass_plan(w.ctypes.data, len(w), max_points, out.ctypes.data, C.byref(npasses)))
+    return out, int(npasses.value)
+
+
+def pass_select(pts_ptr: int, n: int, grid: ShardGrid, pass_of_cell_ptr: int, pass_no: int, out_ptr: int, room: int,
+                rel=(), device: int = 0):
+    """pcc_pass_select on device pointers: the points of pass `pass_no`'s cells
+    compacted into out_ptr in input order.  Returns (kept, below) with below[j]
+    = selected points with index < rel[j] (rel ascending, within [0, n])."""
+    r = np.ascontiguousarray(rel, dtype=np.uint64)
+    below = np.zeros(len(r), dtype=np.uint64)
+    kept = C.c_uint64(0)
+    _check(lib().pcc_pass_select(C.c_void_p(pts_ptr), n, C.byref(grid), C.c_void_p(pass_of_cell_ptr), pass_no,
+                                 C.c_void_p(out_ptr), room, C.byref(kept), r.ctypes.data, len(r), below.ctypes.data,
+                                 device))
+    return int(kept.value), below
+
+
+def convert_from_paths(paths, output: str, batch_size: int = 10_000, device: int = 0,
+                       max_resident_points: int | None = None, config: dict | None = None):
+    """lib.rs:11-60 convert_from_paths.  With max_resident_points (a cap on the
+    points held in device memory) the cloud is converted in level-0 subtree
+    passes (pcc_convert_files_passes) and the pass report is returned as a dict."""
     arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
-    opt = default_options(batch_size=batch_size, device=device)
-    _check(lib().pcc_convert_files(os.fsencode(output), arr, len(paths), C.byref(opt)))
+    opt = default_options(batch_size=batch_size, device=device, **(config or {}))
+    if max_resident_points is None:
+        _check(lib().pcc_convert_files(os.fsencode(output), arr, len(paths), C.byref(opt)))
+        return None
+    rep = PassReport()
+    _check(lib().pcc_convert_files_passes(os.fsencode(output), arr, len(paths), C.byref(opt), max_resident_points,
+                                          C.byref(rep)))
+    return rep.as_dict()
 
 
 def write_ply(path: str, pts: np.ndarray, ascii: bool = False):
